@@ -1,8 +1,18 @@
 """Throughput benchmark of the vectorised Futbol env step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B] [--players 2] [--kind v1|v0]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and the episode statistics).
+--full adds the measurements that take runs of their own: `roofline` (the per-kernel timings and
+the stream-copy ceiling), `cpu_baseline` and the `open_loop_rollout` companion line.  The envs
+take the same steps before the timed region either way, so both runs time the same K steps.
+--dump-outputs DIR writes what the last timed step returned (obs, reward, done,
+terminal_observation) to DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
 
 Workload (BASELINE.json configs[1]/[3]): B = 65 536 independent 2v2 envs_v1
 matches per GPU, synthetic random left-team actions (Philox, generated on the
@@ -17,7 +27,7 @@ GPU, env shards with global env ids rank*B..; weak scaling; one RCCL
 all_reduce(SUM) of [episode-return sum, episodes, env-steps] every 300 steps
 (the only collective: the envs never exchange anything).
 
-Prints ONE JSON line (rank 0).  `roofline` is the step kernel's algorithmic
+Prints ONE JSON line (rank 0).  With --full, `roofline` is the step kernel's algorithmic
 HBM bytes (579 B per 2v2 env-step) / its average duration,
 measured live with HIP events on the launch stream; `cpu_baseline` times the
 oracle/ C restatement of the same step on the host (kind "port": the
@@ -205,7 +215,7 @@ def rollout_companion(args):
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--envs", str(args.envs), "--players", str(args.players), "--kind", args.kind, "--rollout", "100",
-           "--no-cpu-baseline", "--no-rollout-line", "--stagger", str(args.stagger)]
+           "--full", "--no-cpu-baseline", "--no-rollout-line", "--stagger", str(args.stagger)]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         ln = [x for x in out.stdout.splitlines() if x.startswith("{")][-1]
@@ -333,6 +343,33 @@ def stamps_report(venv, one_step, args):
     venv.close()
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: upper bound of everything written
+
+
+def dump_outputs(path, outs, rank, world):
+    """--dump-outputs: the last timed step's (obs, reward, done, terminal_observation) of this rank's
+    envs, each [B, ...] on the device, as float32 <name>.npy files under `path` (<name>_rank<r>.npy in
+    a multi-rank run).  terminal_observation is defined only where done is set; its other rows are
+    written as zeros.  Outputs larger than DUMP_MAX_BYTES in all are cut down to a fixed, seeded
+    sample of env rows, the same rows in every array, listed in env_index.npy."""
+    obs, rew, done, term = outs
+    B = int(obs.shape[0])
+    per_env = 4 * (2 * int(obs[0].numel()) + 2) + 8
+    idx = None
+    if per_env * B > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - 4096) // per_env)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    mask = done.to(torch.bool).reshape((B,) + (1,) * (term.dim() - 1))
+    arrays = {"obs": obs, "reward": rew, "done": done, "terminal_observation": torch.where(mask, term, torch.zeros_like(term))}
+    os.makedirs(path, exist_ok=True)
+    tag = "_rank%d" % rank if world > 1 else ""
+    for name, t in arrays.items():
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + tag + ".npy"), a if idx is None else a[idx])
+    if idx is not None:
+        np.save(os.path.join(path, "env_index" + tag + ".npy"), idx.astype(np.float64))
+
+
 def launch_ranks(n, argv):
     """`--gpus N` (N > 1) without an external launcher: N child processes of this same script, rank r
     on LOCAL_RANK r (its GPU), rendezvous at 127.0.0.1 on a free port -- what torchrun would set up.
@@ -413,11 +450,19 @@ def main():
     ap.add_argument("--rollout", type=int, default=0,
                     help="N > 0: step with open-loop rollout launches of up to N steps each (futbol_rollout: the "
                          "synthetic actions do not depend on the observations), instead of one launch per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel roofline figures and the "
+                         "stream-copy ceiling, the CPU baselines, the open-loop rollout companion line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's obs / reward / done / "
+                         "terminal_observation to DIR/<name>.npy (float32)")
     ap.add_argument("--no-rollout-line", action="store_true",
-                    help="skip the open_loop_rollout companion measurement (a child bench.py --rollout 100 run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the open_loop_rollout companion measurement (a child bench.py "
+                         "--rollout 100 run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline runs")
     ap.add_argument("--profile-steps", type=int, default=600,
-                    help="steps timed per-kernel with HIP events (a multiple of the episode length)")
+                    help="steps timed per-kernel with HIP events under --full (a multiple of the episode "
+                         "length); twice as many steps precede the timed region, with or without --full")
     ap.add_argument("--snapshots", type=int, default=24, help="--stamps: single-launch wave snapshots")
     ap.add_argument("--snapshot-stride", type=int, default=5, help="--stamps: steps between snapshots")
     ap.add_argument("--stamps-dump", default="",
@@ -427,6 +472,8 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launcher-selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.direct and args.rollout:
         ap.error("--direct launches one futbol_step per step; it cannot be combined with --rollout")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -486,11 +533,15 @@ def main():
         one_step()
     torch.cuda.synchronize(dev)
 
+    # The envs take 2 x profile_steps more steps before the timed region: `profile_steps` launches on
+    # pre-generated actions, then as many with a fill launch before each.  --full times them, the
     # per-kernel timing of the dominant kernel (the env step), two ways, over whole episodes
     # (all envs start together, so the per-step cost varies with the episode phase):
     #  (1) HIP events around a hipGraph of `profile_steps` back-to-back step launches with
     #      pre-generated actions (the way the kernel runs in the timed region) -> kernel_ms
     #  (2) events stamped by each dispatch (hipExtLaunchKernelGGL)           -> kernel_ms_dispatch
+    # A plain run makes the same launches one by one, untimed, so that its timed region starts from
+    # the same env states as a --full run's.
     acts = torch.empty((args.profile_steps,) + tuple(act.shape), dtype=torch.uint8, device=dev)
     for t in range(args.profile_steps):
         venv.random_actions(10**6 + t, seed=1234, out=acts[t])
@@ -498,40 +549,52 @@ def main():
     rbuf = None
     if RL:  # the rollout launches' output buffers [RL, B, ...] (reused by every launch)
         rbuf = venv.rollout(acts[:min(RL, args.profile_steps)].contiguous())
-    kg = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(stream)
-    with torch.cuda.stream(s):
-        with torch.cuda.graph(kg, stream=s):
-            if RL:
-                for t0_ in range(0, args.profile_steps, RL):
-                    n_ = min(RL, args.profile_steps - t0_)
-                    venv.rollout(acts[t0_:t0_ + n_], out=tuple(b[:n_] for b in rbuf))
-            else:
-                for t in range(args.profile_steps):
-                    venv.step_raw(acts[t])
-    stream.wait_stream(s)
-    torch.cuda.synchronize(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    kg.replay()
-    e1.record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms = e0.elapsed_time(e1) / args.profile_steps
-    del kg, acts
-    venv.kernel_timing(True)
+
+    def profile_launches():
+        if RL:
+            for t0_ in range(0, args.profile_steps, RL):
+                n_ = min(RL, args.profile_steps - t0_)
+                venv.rollout(acts[t0_:t0_ + n_], out=tuple(b[:n_] for b in rbuf))
+        else:
+            for t in range(args.profile_steps):
+                venv.step_raw(acts[t])
+
+    kernel_ms = kernel_ms_dispatch = None
+    if args.full:
+        kg = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(stream)
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(kg, stream=s):
+                profile_launches()
+        stream.wait_stream(s)
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        kg.replay()
+        e1.record(stream)
+        torch.cuda.synchronize(dev)
+        kernel_ms = e0.elapsed_time(e1) / args.profile_steps
+        del kg
+        venv.kernel_timing(True)
+    else:
+        profile_launches()
+        torch.cuda.synchronize(dev)
+    del acts
     if RL:
         a_ = venv.random_actions_steps(min(RL, args.profile_steps), ALL, seed=1234)
         for _ in range(max(1, args.profile_steps // RL)):
             venv.rollout(a_, out=tuple(b[:a_.shape[0]] for b in rbuf))
-        tot_ms, cnt = venv.kernel_timing(False)
-        kernel_ms_dispatch = tot_ms / max(cnt * a_.shape[0], 1)
+        if args.full:
+            tot_ms, cnt = venv.kernel_timing(False)
+            kernel_ms_dispatch = tot_ms / max(cnt * a_.shape[0], 1)
         del a_
     else:
         for _ in range(args.profile_steps):
             one_step()
-        tot_ms, cnt = venv.kernel_timing(False)
-        kernel_ms_dispatch = tot_ms / max(cnt, 1)
+        if args.full:
+            tot_ms, cnt = venv.kernel_timing(False)
+            kernel_ms_dispatch = tot_ms / max(cnt, 1)
 
     if args.stamps:
         return stamps_report(venv, one_step, args)
@@ -699,12 +762,16 @@ def main():
 
     total_env_steps = B * args.steps * world
     value = total_env_steps / elapsed
-    out_bytes = 4
-    per_env = algo_bytes_per_env_step(args.kind, n, out_bytes)
-    achieved = per_env * B / (kernel_ms * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic(args.kind, n, B)
+    if args.dump_outputs:
+        # what the last timed step returned: the env buffers step_raw wrote, or (rollout launches) the
+        # last written slice of the rollout buffers; env groups in env-id order
+        if RL and graphs is not None:
+            k = (chunks[-1][1] - 1) % RL
+            outs = [tuple(b[k] for b in rbufs[id(ge)]) for ge in groups]
+        else:
+            outs = [(ge._obs, ge._rew, ge._done, ge._term) for ge in groups]
+        dump_outputs(args.dump_outputs, tuple(torch.cat(x) for x in zip(*outs)), rank, world)
     ndev = D.distinct_devices(dev)
-    ceil = copy_ceiling(dev) if rank == 0 else None
     line = {
         "metric": metric_of(args.kind, n, B), "value": value, "unit": "env-steps/s", "n_gpus": ndev,
         "ranks": world, "steps": args.steps,
@@ -727,25 +794,33 @@ def main():
                    % venv.episode_steps,
                    "envs_per_gpu": B, "global_envs": B * world, "parallelism": "dp%d" % world,
                    "obs_dtype": "f32", "hip_graph": bool(graphs is not None), "env_groups": ngroups},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "copy_ceiling_gbs": ceil["gbs"] if ceil else None,
-                     "frac_of_copy_ceiling": achieved / ceil["gbs"] if ceil else None,
-                     "copy_ceiling": ceil,
-                     "kernel": "v1_step_kernel<%d,float>" % n if args.kind == "v1" else "v0_step_kernel<float>",
-                     "kernel_ms": kernel_ms, "kernel_ms_dispatch_events": kernel_ms_dispatch,
-                     "kernel_timing": ("HIP events around a hipGraph of %d back-to-back step launches"
-                                       % args.profile_steps) if not RL else
-                                      ("HIP events around a hipGraph of %d steps as rollout launches of %d steps; "
-                                       "per step" % (args.profile_steps, RL)),
-                     "algo_bytes_per_launch": per_env * B,
-                     "algo_bytes_per_env_step": per_env, "traffic_source": traffic_src},
         "episodes": {"finished": float(stats[1]),
                      "mean_return": float(stats[0] / stats[1]) if stats[1] else None},
+        "full": bool(args.full),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out_bytes = 4
+        per_env = algo_bytes_per_env_step(args.kind, n, out_bytes)
+        achieved = per_env * B / (kernel_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(args.kind, n, B)
+        ceil = copy_ceiling(dev) if rank == 0 else None
+        line["roofline"] = {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "copy_ceiling_gbs": ceil["gbs"] if ceil else None,
+            "frac_of_copy_ceiling": achieved / ceil["gbs"] if ceil else None,
+            "copy_ceiling": ceil,
+            "kernel": "v1_step_kernel<%d,float>" % n if args.kind == "v1" else "v0_step_kernel<float>",
+            "kernel_ms": kernel_ms, "kernel_ms_dispatch_events": kernel_ms_dispatch,
+            "kernel_timing": ("HIP events around a hipGraph of %d back-to-back step launches"
+                              % args.profile_steps) if not RL else
+                             ("HIP events around a hipGraph of %d steps as rollout launches of %d steps; "
+                              "per step" % (args.profile_steps, RL)),
+            "algo_bytes_per_launch": per_env * B,
+            "algo_bytes_per_env_step": per_env, "traffic_source": traffic_src}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.kind, n)
-    if rank == 0 and world == 1 and not RL and not args.no_rollout_line and args.graph:
+    if args.full and rank == 0 and world == 1 and not RL and not args.no_rollout_line and args.graph:
         line["open_loop_rollout"] = rollout_companion(args)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -13,7 +13,7 @@ for spec in $AB; do
   v=${spec%%:*}; args=${spec#*:}; args=${args//,/ }
   i=$((i+1))
   if [ "$v" = main ]; then lv=""; else lv=$v; fi
-  FUTBOL_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --no-cpu-baseline --no-rollout-line $args > $O/b${i}_$v.log 2>&1 || { echo bench $spec failed; exit 1; }
+  FUTBOL_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-rollout-line $args > $O/b${i}_$v.log 2>&1 || { echo bench $spec failed; exit 1; }
   echo "$spec $(grep -o '"value": [0-9.e+]*' $O/b${i}_$v.log) $(grep -o '"kernel_ms": [0-9.e+-]*' $O/b${i}_$v.log)"
 done
 echo rc=0

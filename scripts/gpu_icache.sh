@@ -9,6 +9,6 @@ C="SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQC_ICACHE_REQ 
 for cfg in "c2:" "c5:--players 5" "c3:--kind v0"; do
   t=${cfg%%:*}; a=${cfg#*:}
   timeout -s KILL 120 rocprofv3 --pmc $C -d $OUT/$t -o run --output-format csv -- python3 $R/bench.py --steps 300 --warmup 20 \
-      --no-cpu-baseline --no-rollout-line --profile-steps 20 --graph 0 $a > $OUT/$t.log 2>&1 || { echo "pass $t failed"; exit 1; }
+      --full --no-cpu-baseline --no-rollout-line --profile-steps 20 --graph 0 $a > $OUT/$t.log 2>&1 || { echo "pass $t failed"; exit 1; }
 done
 echo icache rc=0

@@ -3,7 +3,7 @@
 #   gpurun --timeout 1200 -- bash scripts/gpu_steps.sh <steps-file> <out-dir> [section]
 # Each non-empty, non-# line of <steps-file> is "NAME TIMEOUT_S COMMAND...", e.g.
 #   suite   600  python -u -m pytest tests -m gpu -x -q --timeout 250 --timeout-method thread
-#   b_kx6   200  env FUTBOL_LIB_VARIANT=kx6 python bench.py --no-cpu-baseline --players 5
+#   b_kx6   200  env FUTBOL_LIB_VARIANT=kx6 python bench.py --full --no-cpu-baseline --players 5
 # A line "[name]" starts a section: with a [section] argument only that section's steps run (a round's
 # calls live in one file, scripts/steps/rNN.txt, one section per call); without one, every step runs.
 # Output of step NAME goes to <out-dir>/NAME.log; <out-dir>/steps.txt lists every step's status.

@@ -92,6 +92,40 @@ def test_metric_labels_per_config():
     assert bench.workload_of("v0", 2, 65536, 1).startswith("C3:")
 
 
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    # --dump-outputs: float32 arrays of the last step's outputs; terminal_observation only where done
+    import numpy as np
+    import torch
+    B = 37
+    g = torch.Generator().manual_seed(0)
+    obs, term = torch.rand((B, 20), generator=g), torch.rand((B, 20), generator=g)
+    rew = torch.rand(B, generator=g)
+    done = (torch.arange(B) % 3 == 0).to(torch.uint8)
+    term[1] = float("nan")  # a row that is not done may hold anything
+    bench.dump_outputs(str(tmp_path / "a"), (obs, rew, done, term), 0, 1)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("obs", "reward", "done", "terminal_observation")}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(n + ".npy" for n in got)
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["obs"], obs.numpy()) and np.array_equal(got["reward"], rew.numpy())
+    assert np.array_equal(got["done"], done.numpy().astype(np.float32))
+    d = done.numpy().astype(bool)
+    assert np.array_equal(got["terminal_observation"][d], term.numpy()[d])
+    assert not got["terminal_observation"][~d].any()
+    # outputs past the size limit: the same seeded sample of env rows in every array, within the limit
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 6000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), (obs, rew, done, term), 1, 2)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert files == sorted(n + "_rank1.npy" for n in list(got) + ["env_index"])
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= 6000
+    idx = np.load(str(tmp_path / "b" / "env_index_rank1.npy"))
+    assert idx.dtype == np.float64 and 0 < len(idx) < B and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "obs_rank1.npy")), obs.numpy()[idx.astype(int)])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "reward_rank1.npy")), rew.numpy()[idx.astype(int)])
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f)), equal_nan=True)
+
+
 def test_c1_line():
     import json
     import subprocess

@@ -90,6 +90,28 @@ def _sched_flags(src):
     if not SCHED or b not in SCHED_SOURCES:
         return []
     return ["-mllvm", "-amdgpu-sched-strategy=" + SCHED]
+
+
+# Kernel-argument preloading: the by-value single-step kernels (N <= 4: futbol_v1_impl.hpp
+# by_value::v1_step_kernel; futbol_v0.hip v0_step_kernel) take their launch scalars (B, env_base, seed) and
+# the pointers of their first loads as the 14 leading dwords of the kernel arguments; with this option the
+# code object asks the hardware to deliver those in user SGPRs at wave start, so the first state loads
+# issue without waiting for a scalar load of the argument segment.  (The compiler keeps a 256-byte
+# compatibility prologue, s_load + s_waitcnt + s_branch, in front of the entry for firmware without the
+# feature.)  A TU is listed only if it builds at gate variant 0 with no finding and
+# tests/test_kernarg_preload.py holds for it.  N = 3 builds clean but is left out: in its f64 instance the
+# scheduler (LLVM's default for this TU, see SCHED_SOURCES) hoists the scalar load of the later arguments
+# to the entry and waits for it before the first state load, so the preload buys that instance nothing.
+# N >= 5 keeps the kernels that read the scalars through the params pointer (kArgsByValue): nothing to
+# preload.  FUTBOL_PRELOAD=0 builds without the option (the A/B of the flag alone).
+PRELOAD = os.environ.get("FUTBOL_PRELOAD", "16")
+PRELOAD_SOURCES = {"futbol_v1_n%d_e64.hip" % n for n in (1, 2, 4)} | {"futbol_v0.hip"}
+
+
+def _preload_flags(src):
+    if PRELOAD in ("", "0") or os.path.basename(src) not in PRELOAD_SOURCES:
+        return []
+    return ["-mllvm", "-amdgpu-kernarg-preload-count=" + PRELOAD]
 # A/B of compiler options: FUTBOL_EXTRA_CFLAGS="..." (with a FUTBOL_BUILD_VARIANT name)
 CFLAGS += os.environ.get("FUTBOL_EXTRA_CFLAGS", "").split()
 # Diagnostic defines, selected explicitly: a variant named exactly "stamps" / "crumbs" / "bounds", or a
@@ -163,7 +185,8 @@ def _compile(src, force):
     """One TU.  Its full command line is stamped next to the object (<obj>.cmd): a build with other
     flags (the env-var knobs above) recompiles instead of reusing an object built differently."""
     obj = os.path.join(OBJ, os.path.basename(src) + ".o")
-    base = [HIPCC] + CFLAGS + _phi_flags(src) + _sched_flags(src) + _big_flags(src) + _tu_flags(src)
+    base = ([HIPCC] + CFLAGS + _phi_flags(src) + _sched_flags(src) + _preload_flags(src) + _big_flags(src) +
+            _tu_flags(src))
     stamp = obj + ".cmd"
     try:
         with open(stamp) as f:

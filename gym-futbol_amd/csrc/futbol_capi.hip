@@ -39,6 +39,7 @@ struct FutbolCtx {
     int epw = 64;     // envs per one-wave block of the v1 kernels
     int v1_def = 0;   // the default-field (compile-time geometry) kernel applies
     void* d_params = nullptr;
+    StepArgs sa{};    // host copy of the params' launch scalars (fixed at create), passed to the step kernels by value
     char* d_state = nullptr;
     size_t state_bytes = 0;
     std::vector<Field> fields;
@@ -302,6 +303,7 @@ extern "C" int futbol_create(const FutbolConfig* cfg, int32_t device, uint64_t s
         if ((he = hipMalloc(&ctx->d_params, sizeof(V1Params))) != hipSuccess) return bail(he, "hipMalloc(params)");
         if ((he = hipMemcpy(ctx->d_params, &hp, sizeof(hp), hipMemcpyHostToDevice)) != hipSuccess)
             return bail(he, "hipMemcpy(params)");
+        ctx->sa = step_args(hp);
         V1Ptrs& s = ctx->v1;
         s.pxy = (double2*)fptr("pxy");
         s.vxy = (double2*)fptr("vxy");
@@ -329,7 +331,7 @@ extern "C" int futbol_create(const FutbolConfig* cfg, int32_t device, uint64_t s
         memset(ctx->d_stamps, 0, (size_t)((B + 63) / 64 + 1) * kStampStride * 8);
         s.stamps = ctx->d_stamps;
 #endif
-        int rc = launch_v1(N, ctx->epw, ctx->v1_def, (const V1Params*)ctx->d_params, B, s, 0, 1, nullptr, nullptr, nullptr,
+        int rc = launch_v1(N, ctx->epw, ctx->v1_def, (const V1Params*)ctx->d_params, ctx->sa, s, 0, 1, nullptr, nullptr, nullptr,
                            nullptr, nullptr, nullptr, 1, 1, 0);
         if (rc) return bail(hipGetLastError(), "launch(init)");
     } else {
@@ -338,6 +340,7 @@ extern "C" int futbol_create(const FutbolConfig* cfg, int32_t device, uint64_t s
         if ((he = hipMalloc(&ctx->d_params, sizeof(V0Params))) != hipSuccess) return bail(he, "hipMalloc(params)");
         if ((he = hipMemcpy(ctx->d_params, &hp, sizeof(hp), hipMemcpyHostToDevice)) != hipSuccess)
             return bail(he, "hipMemcpy(params)");
+        ctx->sa = step_args(hp);
         V0Ptrs& s = ctx->v0;
         s.row = (double2*)fptr("row2");
         s.view = (double2*)fptr("view2");
@@ -347,7 +350,7 @@ extern "C" int futbol_create(const FutbolConfig* cfg, int32_t device, uint64_t s
         s.stat_ret = (double*)fptr("stat_ret");
         s.stat_cnt = (uint32_t*)fptr("stat_cnt");
         s.invalid = ctx->d_invalid;
-        int rc = launch_v0((const V0Params*)ctx->d_params, B, s, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
+        int rc = launch_v0((const V0Params*)ctx->d_params, ctx->sa, s, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
                            nullptr, 1, 1, 0);
         if (rc) return bail(hipGetLastError(), "launch(init)");
     }
@@ -451,10 +454,10 @@ static int launch(FutbolCtx* ctx, int what, const uint8_t* actions, const uint8_
     }
     int rc;
     if (ctx->cfg.env_kind == FUTBOL_ENV_V1)
-        rc = launch_v1(ctx->N, ctx->epw, ctx->v1_def, (const V1Params*)ctx->d_params, ctx->B, ctx->v1, out64, what, actions,
+        rc = launch_v1(ctx->N, ctx->epw, ctx->v1_def, (const V1Params*)ctx->d_params, ctx->sa, ctx->v1, out64, what, actions,
                        mask, obs, reward, done, term, 0, nsteps, (hipStream_t)stream);
     else
-        rc = launch_v0((const V0Params*)ctx->d_params, ctx->B, ctx->v0, out64, what, actions, mask, obs, reward,
+        rc = launch_v0((const V0Params*)ctx->d_params, ctx->sa, ctx->v0, out64, what, actions, mask, obs, reward,
                        done, term, 0, nsteps, (hipStream_t)stream);
     g_launch_events = LaunchEvents{};
     if (rc) {

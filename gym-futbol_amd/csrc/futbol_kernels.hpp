@@ -55,6 +55,24 @@ struct V0Params {
     int auto_reset;
 };
 
+// The launch scalars of a context: written once at futbol_create (the C ABI has no setter), kept on
+// the host in FutbolCtx and passed to the step kernels BY VALUE.  A wave's first state loads then
+// depend on the kernel-argument segment alone (preloaded into SGPRs where the TU is built with
+// -amdgpu-kernarg-preload-count, build.py) instead of on a second, dependent scalar load through
+// the params pointer.  The reset kernels (not hot) keep reading them from the device params.
+struct StepArgs {
+    int B;
+    uint32_t env_base;                            // global id of env 0
+    uint64_t seed;
+    int K_done;
+    int auto_reset;
+};
+template <typename Params>
+inline StepArgs step_args(const Params& p)
+{
+    return StepArgs{p.B, p.env_base, p.seed, p.K_done, p.auto_reset};
+}
+
 // Kernel timing (futbol_kernel_timing): when `start` is set, the next env-step launch
 // goes through hipExtLaunchKernelGGL, whose events are stamped by the dispatch itself
 // (kernel begin / end, no marker packets around it).  Set by the C ABI, host thread-local.
@@ -74,9 +92,10 @@ inline void launch_kernel(void (*k)(KArgs...), dim3 grid, dim3 block, hipStream_
         hipLaunchKernelGGL(k, grid, block, 0, stream, static_cast<KArgs>(args)...);
 }
 
-// P: device pointer to the context's V1Params (wave-uniform scalar loads).  what 0 = step (nsteps
-// consecutive steps per launch: the open-loop rollout, futbol_rollout), 1 = reset
-int launch_v1(int N, int epw, int def, const V1Params* P, int B, const V1Ptrs& st, int out64, int what,
+// P: device pointer to the context's V1Params (wave-uniform scalar loads: the reset kernels and the
+// runtime-geometry step instance); sa: the same context's launch scalars, by value (step kernels).
+// what 0 = step (nsteps consecutive steps per launch: the open-loop rollout, futbol_rollout), 1 = reset
+int launch_v1(int N, int epw, int def, const V1Params* P, const StepArgs& sa, const V1Ptrs& st, int out64, int what,
               const uint8_t* actions, const uint8_t* mask, void* obs, void* reward, uint8_t* done, void* term,
               int init, int nsteps, hipStream_t stream);
 int v1_supported(int N);
@@ -85,7 +104,7 @@ size_t v1_spill_slots(int N);
 int layout_v1(int N, int32_t* o);  // 8 values, futbol_solver_layout
 bool v1_is_default_geometry(int N, const V1Params& p);
 
-int launch_v0(const V0Params* P, int B, const V0Ptrs& st, int out64, int what, const uint8_t* actions,
+int launch_v0(const V0Params* P, const StepArgs& sa, const V0Ptrs& st, int out64, int what, const uint8_t* actions,
               const uint8_t* mask, void* obs, void* reward, uint8_t* done, void* term, int init, int nsteps,
               hipStream_t stream);
 

@@ -69,6 +69,28 @@ struct V1Ptrs {
     unsigned long long* stamps;   // diagnostic builds only (FUTBOL_STAMPS): [blocks][16] cycle sums
 };
 
+// The step kernels take the pointers of their first loads (meta and the body / row arrays) as
+// separate leading kernel arguments, which the hardware can preload into SGPRs (struct arguments
+// are not preloaded), and the rest of the struct, first used late in the step, as this tail.
+struct V1PtrsTail {
+    double* ep_ret;
+    uint16_t* ckey;
+    double* cjn;
+    double* stat_ret;
+    uint32_t* stat_cnt;
+    double* spill;
+    unsigned long long* invalid;
+    unsigned long long* stamps;
+};
+__host__ __device__ inline V1PtrsTail v1_tail(const V1Ptrs& s)
+{
+    return V1PtrsTail{s.ep_ret, s.ckey, s.cjn, s.stat_ret, s.stat_cnt, s.spill, s.invalid, s.stamps};
+}
+__host__ __device__ inline V1Ptrs v1_join(uint64_t* meta, double2* pxy, double2* vxy, double2* bxy, const V1PtrsTail& t)
+{
+    return V1Ptrs{pxy, vxy, bxy, meta, t.ep_ret, t.ckey, t.cjn, t.stat_ret, t.stat_cnt, t.spill, t.invalid, t.stamps};
+}
+
 struct V0Ptrs {
     double2* row;   // [13][B]: (row entry 2q, 2q + 1) pairs of the [25] rows (entry 25: pad)
     double2* view;  // [4][B]: (x, y) of each frozen view
@@ -79,5 +101,20 @@ struct V0Ptrs {
     uint32_t* stat_cnt;
     unsigned long long* invalid;
 };
+struct V0PtrsTail {
+    double* ep_ret;
+    uint32_t* score;
+    double* stat_ret;
+    uint32_t* stat_cnt;
+    unsigned long long* invalid;
+};
+__host__ __device__ inline V0PtrsTail v0_tail(const V0Ptrs& s)
+{
+    return V0PtrsTail{s.ep_ret, s.score, s.stat_ret, s.stat_cnt, s.invalid};
+}
+__host__ __device__ inline V0Ptrs v0_join(uint64_t* meta, double2* row, double2* view, const V0PtrsTail& t)
+{
+    return V0Ptrs{row, view, meta, t.ep_ret, t.score, t.stat_ret, t.stat_cnt, t.invalid};
+}
 
 }  // namespace futbol

@@ -516,14 +516,17 @@ __device__ __forceinline__ void store(const V0Ptrs& st, int env, int B, const En
 using namespace v0;
 
 // FutbolEnv.step (:628-717) + DummyVecEnv auto-reset
-template <typename OT>
-__device__ __forceinline__ void v0_step_body(const V0Params* __restrict__ P, const V0Ptrs& st,
+// P: the context's device params (the constructor's kwargs); R: its launch scalars -- the kernel's own
+// arguments (StepArgs: v0_step_kernel, whose state loads then wait for no load through P) or P itself
+// (v0_rollout_kernel)
+template <typename OT, typename RT>
+__device__ __forceinline__ void v0_step_body(const V0Params* __restrict__ P, const RT* __restrict__ R, const V0Ptrs& st,
                                              const uint8_t* __restrict__ actions, OT* __restrict__ obs,
                                              OT* __restrict__ reward, uint8_t* __restrict__ done_out,
                                              OT* __restrict__ term_obs)
 {
     const int env = blockIdx.x * 64 + threadIdx.x;
-    const int B = P->B;
+    const int B = R->B;
     if (env >= B) return;
     Env e;
     Meta m;
@@ -532,7 +535,7 @@ __device__ __forceinline__ void v0_step_body(const V0Params* __restrict__ P, con
     const bool row_valid_before = m.bit(kRowValid);
     const uint32_t ev = m.event();
     m.set_event(ev + 1);
-    Stream rs(P->seed, P->env_base + (uint32_t)env, ev, 0);
+    Stream rs(R->seed, R->env_base + (uint32_t)env, ev, 0);
     const Ctx c{P, st.view, env, B, &rs};
 
     int a0, a1, bad = 0;
@@ -640,17 +643,17 @@ __device__ __forceinline__ void v0_step_body(const V0Params* __restrict__ P, con
         }
     }
     const uint32_t steps = m.steps();
-    if ((int)steps + 1 >= P->K_done) done = true;  // time >= game_time, checked before time += 0.1
+    if ((int)steps + 1 >= R->K_done) done = true;  // time >= game_time, checked before time += 0.1
     m.set_steps(steps + 1 > (uint32_t)kMaxSteps ? (uint32_t)kMaxSteps : steps + 1);
 
     double ret = ep_ret0 + rw;
     bool row_valid = true;
-    if (done && !P->auto_reset) {
+    if (done && !R->auto_reset) {
         st.stat_ret[env] = st.stat_ret[env] + ret;
         st.stat_cnt[env] = st.stat_cnt[env] + 1;
         ret = 0.0;
     }
-    if (done && P->auto_reset) {
+    if (done && R->auto_reset) {
         if (term_obs) write_obs<OT>(e, true, term_obs + (size_t)env * 30);
         st.stat_ret[env] = st.stat_ret[env] + ret;
         st.stat_cnt[env] = st.stat_cnt[env] + 1;
@@ -675,24 +678,36 @@ __device__ __forceinline__ void v0_step_body(const V0Params* __restrict__ P, con
     if (bad) atomicAdd(st.invalid, (unsigned long long)bad);
 }
 
-// ROLL (nsteps > 1): open-loop rollout (futbol_rollout), step k on the k-th [B][...] slice of every
-// buffer; the single-step instance has no loop around the body
-template <typename OT, bool ROLL>
-__global__ void __launch_bounds__(64) v0_step_kernel(const V0Params* __restrict__ P, V0Ptrs st,
-                                                     const uint8_t* __restrict__ actions, OT* __restrict__ obs,
-                                                     OT* __restrict__ reward, uint8_t* __restrict__ done_out,
-                                                     OT* __restrict__ term_obs, int nsteps)
+// The open-loop rollout (futbol_rollout, nsteps > 1): step k on the k-th [B][...] slice of every buffer.
+// It reads the launch scalars through P (that trip is paid once per launch of nsteps steps).
+template <typename OT>
+__global__ void __launch_bounds__(64) v0_rollout_kernel(const V0Params* __restrict__ P, V0Ptrs st,
+                                                        const uint8_t* __restrict__ actions, OT* __restrict__ obs,
+                                                        OT* __restrict__ reward, uint8_t* __restrict__ done_out,
+                                                        OT* __restrict__ term_obs, int nsteps)
 {
     stage_pow_tables();
-    if constexpr (!ROLL) {
-        v0_step_body<OT>(P, st, actions, obs, reward, done_out, term_obs);
-        return;
-    }
     const size_t B = (size_t)P->B, adim = P->action_as_int ? 1 : 2;
 #pragma unroll 1
     for (int k = 0; k < nsteps; ++k)
-        v0_step_body<OT>(P, st, actions + (size_t)k * B * adim, obs + (size_t)k * B * 30, reward + (size_t)k * B,
+        v0_step_body<OT>(P, P, st, actions + (size_t)k * B * adim, obs + (size_t)k * B * 30, reward + (size_t)k * B,
                          done_out + (size_t)k * B, term_obs ? term_obs + (size_t)k * B * 30 : nullptr);
+}
+
+// The single step (futbol_step): no loop around the body, and the launch scalars by value
+template <typename OT>
+__global__ void __launch_bounds__(64) v0_step_kernel(
+    // the first 14 dwords: what the state loads and the episode end need, plain scalars and pointers
+    // (preloaded into SGPRs at wave start where build.py lists this TU; a struct would not be)
+    int B, uint32_t env_base, uint64_t seed, const uint8_t* __restrict__ actions, uint64_t* meta, double2* row,
+    double2* view, int K_done, int auto_reset,
+    const V0Params* __restrict__ P, V0PtrsTail tail, OT* __restrict__ obs, OT* __restrict__ reward,
+    uint8_t* __restrict__ done_out, OT* __restrict__ term_obs)
+{
+    stage_pow_tables();
+    const StepArgs R{B, env_base, seed, K_done, auto_reset};
+    const V0Ptrs st = v0_join(meta, row, view, tail);
+    v0_step_body<OT>(P, &R, st, actions, obs, reward, done_out, term_obs);
 }
 
 template <typename OT>
@@ -730,26 +745,29 @@ __global__ void __launch_bounds__(64) v0_reset_kernel(const V0Params* __restrict
     store(st, env, B, e, m, false);
 }
 
-int launch_v0(const V0Params* P, int B, const V0Ptrs& st, int out64, int what, const uint8_t* actions,
+int launch_v0(const V0Params* P, const StepArgs& sa, const V0Ptrs& st, int out64, int what, const uint8_t* actions,
               const uint8_t* mask, void* obs, void* reward, uint8_t* done, void* term, int init, int nsteps,
               hipStream_t stream)
 {
+    const int B = sa.B;
     const dim3 grid((B + 63) / 64), block(64);
     if (what == 0) {
-        if (out64) {
-            if (nsteps > 1)
-                launch_kernel(v0_step_kernel<double, true>, grid, block, stream, P, st, actions, (double*)obs,
+        if (nsteps > 1) {
+            if (out64)
+                launch_kernel(v0_rollout_kernel<double>, grid, block, stream, P, st, actions, (double*)obs,
                               (double*)reward, done, (double*)term, nsteps);
             else
-                launch_kernel(v0_step_kernel<double, false>, grid, block, stream, P, st, actions, (double*)obs,
-                              (double*)reward, done, (double*)term, 1);
-        } else {
-            if (nsteps > 1)
-                launch_kernel(v0_step_kernel<float, true>, grid, block, stream, P, st, actions, (float*)obs,
+                launch_kernel(v0_rollout_kernel<float>, grid, block, stream, P, st, actions, (float*)obs,
                               (float*)reward, done, (float*)term, nsteps);
-            else
-                launch_kernel(v0_step_kernel<float, false>, grid, block, stream, P, st, actions, (float*)obs,
-                              (float*)reward, done, (float*)term, 1);
+        } else {
+            // (the argument order of v0_step_kernel; launch_kernel casts the void* buffers to the kernel's OT*)
+            const V0PtrsTail tail = v0_tail(st);
+            auto go = [&](auto kernel) {
+                launch_kernel(kernel, grid, block, stream, sa.B, sa.env_base, sa.seed, actions, st.meta, st.row,
+                              st.view, sa.K_done, sa.auto_reset, P, tail, obs, reward, done, term);
+            };
+            if (out64) go(v0_step_kernel<double>);
+            else go(v0_step_kernel<float>);
         }
     } else {
         if (out64)

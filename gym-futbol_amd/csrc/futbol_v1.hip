@@ -6,7 +6,7 @@
 namespace futbol {
 
 #define FUTBOL_DECL(n)                                                                                    \
-    int launch_v1_n##n##_e64(const V1Params* P, int B, const V1Ptrs& st, int out64, int what, int def,     \
+    int launch_v1_n##n##_e64(const V1Params* P, const StepArgs& sa, const V1Ptrs& st, int out64, int what, int def,     \
                              const uint8_t* a, const uint8_t* mask, void* obs, void* reward, uint8_t* done, \
                              void* term, int init, int nsteps, hipStream_t stream);                   \
     void layout_v1_n##n##_e64(int32_t* o);
@@ -22,7 +22,7 @@ FUTBOL_DECL(9)
 FUTBOL_DECL(10)
 #undef FUTBOL_DECL
 
-int launch_v1(int N, int epw, int def, const V1Params* P, int B, const V1Ptrs& st, int out64, int what,
+int launch_v1(int N, int epw, int def, const V1Params* P, const StepArgs& sa, const V1Ptrs& st, int out64, int what,
               const uint8_t* actions, const uint8_t* mask, void* obs, void* reward, uint8_t* done, void* term,
               int init, int nsteps, hipStream_t stream)
 {
@@ -30,7 +30,7 @@ int launch_v1(int N, int epw, int def, const V1Params* P, int B, const V1Ptrs& s
     switch (N) {
 #define FUTBOL_CASE(n)                                                                                    \
     case n:                                                                                               \
-        return launch_v1_n##n##_e64(P, B, st, out64, what, def, actions, mask, obs, reward, done, term, init, nsteps, \
+        return launch_v1_n##n##_e64(P, sa, st, out64, what, def, actions, mask, obs, reward, done, term, init, nsteps, \
                                     stream);
     FUTBOL_CASE(1) FUTBOL_CASE(2) FUTBOL_CASE(3) FUTBOL_CASE(4) FUTBOL_CASE(5)
     FUTBOL_CASE(6) FUTBOL_CASE(7) FUTBOL_CASE(8) FUTBOL_CASE(9) FUTBOL_CASE(10)

@@ -1975,9 +1975,11 @@ __device__ __forceinline__ void pass_target(const Env<N>& e, Stream& rs, PassDra
 // ---------------------------------------------------------------------------
 // Futbol.step (envs_v1/futbol_env.py:427-483) + DummyVecEnv auto-reset
 // P: geometry / physics constants (a constexpr object in the default-field instance,
-// the context's device copy otherwise); R: the context's device params (runtime fields)
-template <int N, int EPW, typename OT>
-__device__ __forceinline__ void v1_step_body(const V1Params& P, const V1Params* __restrict__ R, Scratch<N, EPW>& sh,
+// the context's device copy otherwise); R: the context's launch scalars (B, env_base, seed, K_done,
+// auto_reset) -- the kernel's own arguments (StepArgs: by_value::v1_step_kernel) or the context's device params
+// (V1Params: v1_step_kernel)
+template <int N, int EPW, typename OT, typename RT>
+__device__ __forceinline__ void v1_step_body(const V1Params& P, const RT* __restrict__ R, Scratch<N, EPW>& sh,
                                              V1Ptrs st, const uint8_t* __restrict__ actions, OT* __restrict__ obs,
                                              OT* __restrict__ reward, uint8_t* __restrict__ done_out,
                                              OT* __restrict__ term_obs)
@@ -2423,6 +2425,46 @@ __global__ void __launch_bounds__(EPW) FUTBOL_V1_STEP_ATTR v1_step_kernel(const 
         }
     }
 }
+
+// The single step (futbol_step) of the small team sizes takes the context's launch scalars (B, env_base,
+// seed, K_done, auto_reset) BY VALUE, in this kernel, instead of reading them through the params pointer as
+// futbol::v1_step_kernel above does: nothing on the way to the first state load then depends on a second scalar
+// load.  Which team sizes: kArgsByValue.
+//  * N >= 5 stays on v1_step_kernel.  The 5v5 instance (~500 VGPRs, SGPRs spilled to VGPR lanes) measured
+//    slower with this signature however the body read the values: 49.5-49.6 us by value, 49.4-49.5 with the
+//    arguments preloaded, 49.7-50.1 through the pointer, against 49.05-49.18 us;
+//    N = 6..10 sit at the 512-VGPR limit with scratch spills.
+//  * The rollouts stay on v1_step_kernel for every N: they pay the extra trip once per launch of nsteps
+//    steps, and with the values live in SGPRs across the step loop the 5v5 and 7v7 rollout instances no
+//    longer built clean (register copies before an exec restore, scripts/isa_exec_check.py).
+template <int N>
+constexpr bool kArgsByValue = N <= 4;
+
+// (futbol::by_value::v1_step_kernel<N, ...>: the profile tools find either kernel as "v1_step_kernel<N,")
+namespace by_value {
+template <int N, int EPW, typename OT, bool DEF>
+__global__ void __launch_bounds__(EPW) FUTBOL_V1_STEP_ATTR v1_step_kernel(
+    // the first 14 dwords, in the order of first use: what the wave's first loads (actions, meta, bodies)
+    // and the shadow-lane clamp need -- plain scalars and pointers, which a TU on build.py's preload
+    // list receives in SGPRs at wave start (a struct argument would not be preloaded)
+    int B, uint32_t env_base, uint64_t seed, const uint8_t* __restrict__ actions, uint64_t* meta, double2* pxy,
+    double2* vxy, double2* bxy,
+    // first used late in the step: one scalar load, waited for where it is needed
+    int K_done, int auto_reset, const V1Params* __restrict__ P, V1PtrsTail tail, OT* __restrict__ obs,
+    OT* __restrict__ reward, uint8_t* __restrict__ done_out, OT* __restrict__ term_obs)
+{
+    static_assert(sizeof(Scratch<N, EPW>) <= 160 * 1024 / 4, "LDS per block");
+    __shared__ Scratch<N, EPW> sh;
+    const V1Ptrs st = v1_join(meta, pxy, vxy, bxy, tail);
+    const StepArgs R{B, env_base, seed, K_done, auto_reset};
+    if constexpr (DEF) {
+        constexpr V1Params G = v1_default_geometry<N>();
+        v1_step_body<N, EPW, OT>(G, &R, sh, st, actions, obs, reward, done_out, term_obs);
+    } else {
+        v1_step_body<N, EPW, OT>(*P, &R, sh, st, actions, obs, reward, done_out, term_obs);
+    }
+}
+}  // namespace by_value
 
 // futbol_create (init=1: Futbol.__init__, which ends in reset()) / futbol_reset (masked)
 template <int N, int EPW, typename OT>

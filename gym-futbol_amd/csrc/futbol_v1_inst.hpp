@@ -11,15 +11,24 @@
 namespace futbol {
 // the step kernel instance for the output type / geometry / rollout flags (ROLL: nsteps > 1)
 template <int N, typename OT>
-inline void launch_v1_step(const V1Params* P, int B, const V1Ptrs& st, int def, const uint8_t* actions, void* obs,
-                           void* reward, uint8_t* done, void* term, int nsteps, hipStream_t stream)
+inline void launch_v1_step(const V1Params* P, const StepArgs& sa, const V1Ptrs& st, int def, const uint8_t* actions,
+                           void* obs, void* reward, uint8_t* done, void* term, int nsteps, hipStream_t stream)
 {
     constexpr int E = 64;
-    const dim3 grid((B + E - 1) / E), block(E);
+    const dim3 grid((sa.B + E - 1) / E), block(E);
     OT *o = (OT*)obs, *r = (OT*)reward, *t = (OT*)term;
     if (nsteps > 1) {
         if (def) launch_kernel(v1_step_kernel<N, E, OT, true, true>, grid, block, stream, P, st, actions, o, r, done, t, nsteps);
         else launch_kernel(v1_step_kernel<N, E, OT, false, true>, grid, block, stream, P, st, actions, o, r, done, t, nsteps);
+    } else if constexpr (kArgsByValue<N>) {
+        // the launch scalars by value, from the context's host copy (argument order: by_value::v1_step_kernel)
+        const V1PtrsTail tail = v1_tail(st);
+        auto go = [&](auto kernel) {
+            launch_kernel(kernel, grid, block, stream, sa.B, sa.env_base, sa.seed, actions, st.meta, st.pxy, st.vxy,
+                          st.bxy, sa.K_done, sa.auto_reset, P, tail, o, r, done, t);
+        };
+        if (def) go(by_value::v1_step_kernel<N, E, OT, true>);
+        else go(by_value::v1_step_kernel<N, E, OT, false>);
     } else {
         if (def) launch_kernel(v1_step_kernel<N, E, OT, true, false>, grid, block, stream, P, st, actions, o, r, done, t, 1);
         else launch_kernel(v1_step_kernel<N, E, OT, false, false>, grid, block, stream, P, st, actions, o, r, done, t, 1);
@@ -29,15 +38,16 @@ inline void launch_v1_step(const V1Params* P, int B, const V1Ptrs& st, int def, 
 
 #define FUTBOL_V1_INSTANCE(NP)                                                                                   \
     namespace futbol {                                                                                           \
-    int launch_v1_n##NP##_e64(const V1Params* P, int B, const V1Ptrs& st, int out64, int what, int def,          \
+    int launch_v1_n##NP##_e64(const V1Params* P, const StepArgs& sa, const V1Ptrs& st, int out64, int what,   \
+                              int def,                                                                           \
                               const uint8_t* actions, const uint8_t* mask, void* obs, void* reward, uint8_t* done, \
                               void* term, int init, int nsteps, hipStream_t stream)                              \
     {                                                                                                            \
         constexpr int N = NP, E = 64;                                                                            \
-        const dim3 grid((B + E - 1) / E), block(E);                                                              \
+        const dim3 grid((sa.B + E - 1) / E), block(E);                                                           \
         if (what == 0) {                                                                                         \
-            if (out64) launch_v1_step<N, double>(P, B, st, def, actions, obs, reward, done, term, nsteps, stream); \
-            else launch_v1_step<N, float>(P, B, st, def, actions, obs, reward, done, term, nsteps, stream);      \
+            if (out64) launch_v1_step<N, double>(P, sa, st, def, actions, obs, reward, done, term, nsteps, stream); \
+            else launch_v1_step<N, float>(P, sa, st, def, actions, obs, reward, done, term, nsteps, stream);     \
         } else {                                                                                                 \
             if (out64)                                                                                           \
                 hipLaunchKernelGGL((v1_reset_kernel<N, E, double>), grid, block, 0, stream, P, st, mask,         \
